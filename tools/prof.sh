@@ -14,7 +14,7 @@ cd "$GRAFT_REPO_ROOT"
 CFG=${1:-cfg2}; shift
 OUT=gpurun_out/prof_$CFG
 mkdir -p $OUT
-CMD="python3 bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-e2e $*"
+CMD="python3 bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-e2e $*"
 SQ="SQ_WAVES,SQ_WAVE_CYCLES,SQ_BUSY_CYCLES,SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_ACTIVE_INST_ANY,SQ_LDS_BANK_CONFLICT,SQ_LDS_IDX_ACTIVE"
 timeout -s KILL 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- $CMD > $OUT/stats.log 2>&1 &&
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- $CMD > $OUT/fetch.log 2>&1 &&
