@@ -339,6 +339,19 @@ func (b *Batch) Wait() error {
 	return toErr(C.pqgpu_batch_wait(b.b, nil, &e), &e)
 }
 
+// CodecStats counts the batch's GZIP data pages by route: inflated on the
+// device by k_inflate or on the host (pqgpu_batch_codec_stats). Members is
+// valid after Sync.
+type CodecStats struct {
+	GzipPages, GzipHostPages, GzipKernelBytes, GzipMembers int64
+}
+
+func (b *Batch) CodecStats() CodecStats {
+	var s C.pqgpu_codec_stats
+	C.pqgpu_batch_codec_stats(b.b, &s)
+	return CodecStats{int64(s.gzip_pages), int64(s.gzip_host_pages), int64(s.gzip_kernel_bytes), int64(s.gzip_members)}
+}
+
 // Status is the error of chunk id alone (nil when it decoded).
 func (b *Batch) Status(id int32) error {
 	var e C.pqgpu_error

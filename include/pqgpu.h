@@ -216,12 +216,16 @@ int pqgpu_batch_reset(pqgpu_batch *b);
 
 /* readChunk + readPages (chunk_reader.go:182-362): walk the chunk's page
  * headers on the host, validate them exactly as the reference does, and
- * stage the page sections for upload. GZIP pages (and dictionary pages) are
- * decompressed on the host; SNAPPY data pages are staged compressed and
- * decompressed by k_snappy at the start of every decode (the host decodes
- * only the page head it validates; PQ_HOST_SNAPPY=1 forces host decoding).
- * A corrupt SNAPPY block is reported at sync as that page's PQ_ERR_DECOMPRESS,
- * in the reference's order (compress.go:102-123). `file_bytes` is the whole file (offsets in `meta`
+ * stage the page sections for upload. Dictionary pages are decompressed on
+ * the host; SNAPPY data pages are staged compressed and decompressed by
+ * k_snappy at the start of every decode (the host decodes only the page head
+ * it validates; PQ_HOST_SNAPPY=1 forces host decoding). GZIP data pages that
+ * take the device route are staged compressed in the same way and inflated by
+ * k_inflate (the host inflates only the page head; PQ_HOST_GZIP=1 forces the
+ * host route, PQ_HOST_GZIP=0 the device route; pages with no bytes, blocks
+ * that do not start 1f 8b 08 and DELTA_LENGTH / DELTA_BYTE_ARRAY pages always
+ * inflate on the host). A corrupt SNAPPY or GZIP block is reported at sync as
+ * that page's PQ_ERR_DECOMPRESS, in the reference's order (compress.go:102-123). `file_bytes` is the whole file (offsets in `meta`
  * are absolute); `col` carries maxD/maxR (schema.go:893-924).
  * A chunk-level error is recorded and returned here; the chunk id is still
  * assigned so its error can be queried later. */
@@ -354,6 +358,15 @@ int pqgpu_batch_copy_group(const pqgpu_batch *b, int32_t chunk_id, int32_t group
  * structure consistently (e.g. leaves of different files). */
 int pqgpu_batch_share_ancestors(pqgpu_batch *b, int32_t chunk_a, int32_t chunk_b, int32_t *equal, pqgpu_error *err);
 int pqgpu_batch_stats_get(const pqgpu_batch *b, pqgpu_batch_stats *out);
+/* GZIP data pages of the batch by route (valid after the chunks are added; gzip_members after sync). */
+typedef struct {
+  int64_t gzip_pages;        /* data pages inflated on the device (k_inflate) */
+  int64_t gzip_host_pages;   /* GZIP pages handed to the host's inflate: data pages that cannot take the
+                              * device route, and dictionary pages */
+  int64_t gzip_kernel_bytes; /* algorithmic bytes of k_inflate: blocks + 2 x raw level bytes + decoded bytes */
+  int64_t gzip_members;      /* gzip members k_inflate decoded in the last synced decode */
+} pqgpu_codec_stats;
+int pqgpu_batch_codec_stats(const pqgpu_batch *b, pqgpu_codec_stats *out);
 /* Diagnostics: 64 device counters filled by in-kernel phase stamps when the
  * environment has PQ_DEBUG_STAMPS=1 at upload time. */
 int pqgpu_batch_debug_counters(pqgpu_batch *b, uint64_t *out64, int reset);
@@ -364,7 +377,7 @@ int pqgpu_batch_debug_counters(pqgpu_batch *b, uint64_t *out64, int reset);
 int pqgpu_batch_kernel_timing(pqgpu_batch *b, int enable);
 int pqgpu_batch_kernel_time(pqgpu_batch *b, double *avg_ms, int64_t *launches, char *name, size_t name_len);
 /* The same for every timed launch slot (0 <= slot < PQGPU_TIMER_SLOTS); PQ_ERR_ARG past the end. */
-#define PQGPU_TIMER_SLOTS 25
+#define PQGPU_TIMER_SLOTS 26
 int pqgpu_batch_kernel_slot(pqgpu_batch *b, int slot, double *avg_ms, int64_t *launches, char *name,
                             size_t name_len);
 /* Algorithmic bytes (sections read + outputs written, counted once) of one launch

@@ -481,6 +481,47 @@ static Status gzip_decode(const uint8_t *src, int64_t n, std::vector<uint8_t> *o
   return Status::Ok();
 }
 
+GzipPrefix::~GzipPrefix() {
+  if (zs) {
+    inflateEnd((z_stream *)zs);
+    delete (z_stream *)zs;
+  }
+}
+bool GzipPrefix::Init(const uint8_t *block, int64_t len, uint8_t *out, int64_t cap) {
+  z_stream *z = new z_stream;
+  memset(z, 0, sizeof(*z));
+  zs = z;
+  if (inflateInit2(z, 16 + MAX_WBITS) != Z_OK) { delete z; zs = nullptr; return false; }
+  src = block;
+  n = len;
+  dst = out;
+  dlen = cap;
+  d = 0;
+  z->next_in = (Bytef *)block;
+  z->avail_in = (uInt)len;
+  return true;
+}
+bool GzipPrefix::Extend(int64_t want) {
+  if (want > dlen) want = dlen;
+  z_stream *z = (z_stream *)zs;
+  if (!z || bad) return false;
+  while (d < want) {
+    z->next_out = dst + d;
+    z->avail_out = (uInt)(want - d);
+    const int rc = inflate(z, Z_SYNC_FLUSH);
+    d = want - (int64_t)z->avail_out;
+    if (rc == Z_STREAM_END) {  // the next member, if any
+      if (z->avail_in == 0 || inflateReset(z) != Z_OK) {
+        if (d < want) bad = true;
+        break;
+      }
+      continue;
+    }
+    if (rc != Z_OK) { bad = true; break; }
+  }
+  return !bad;
+}
+
 Status Decompress(int32_t codec, const uint8_t *src, int64_t n, std::vector<uint8_t> *out) {
   if (codec == 0) {
     out->insert(out->end(), src, src + n);

@@ -117,4 +117,22 @@ struct SnappyPrefix {
   bool Extend(int64_t want);
 };
 
+// The same for a GZIP block (zlib, gzip mode, member after member): the bounded prefix inflate
+// behind the planner's reads of a device-inflated page.
+struct GzipPrefix {
+  void *zs = nullptr;            // z_stream
+  const uint8_t *src = nullptr;
+  int64_t n = 0;
+  uint8_t *dst = nullptr;
+  int64_t dlen = 0, d = 0;       // expected decoded length, bytes decoded so far
+  bool bad = false;
+  GzipPrefix() = default;
+  GzipPrefix(const GzipPrefix &) = delete;
+  GzipPrefix &operator=(const GzipPrefix &) = delete;
+  ~GzipPrefix();
+  bool Init(const uint8_t *block, int64_t len, uint8_t *out, int64_t cap);
+  // Inflate until d >= min(want, dlen). false: the block is corrupt before that byte (or ends).
+  bool Extend(int64_t want);
+};
+
 }  // namespace pq

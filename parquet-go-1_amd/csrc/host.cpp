@@ -389,7 +389,7 @@ static const char *kTimerNames[PQGPU_TIMER_SLOTS] = {
     "k_levels", "k_values_delta", "k_scan_runs", "k_bases", "k_ba_sums", "k_ba_scan",
     "k_ba_emit", "k_records", "k_values_dict", "k_values", "k_delta_prep", "k_snappy", "k_dict_slots",
     "k_nest_count", "k_nest_emit", "k_level_fill", "k_nest_scan", "k_pba", "k_ba_delta", "k_dba_gather",
-    "k_values_copy", "k_group_flat", "k_nest_tile", "k_nest_pcount", "k_nest_tcount"};
+    "k_values_copy", "k_group_flat", "k_nest_tile", "k_nest_pcount", "k_nest_tcount", "k_inflate"};
 
 // The staged page bytes of a batch: grows geometrically without zero-filling, and in a batch
 // with a device context lives in pinned host memory, so upload's H2D copy reads it directly
@@ -444,6 +444,9 @@ struct StageBuf {
   void clear() { n = 0; }
 };
 
+// Default route of GZIP data pages: the device (tools/gzip_probe.py).
+constexpr bool kDevGzipDefault = true;
+
 struct pqgpu_batch {
   pqgpu_ctx *ctx = nullptr;
   std::vector<HostChunk> chunks;
@@ -464,10 +467,19 @@ struct pqgpu_batch {
     uint32_t raw_len, dlen;      // V2 level bytes, decoded length
     uint32_t page;               // global page index
     bool to_values = false;      // plan: k_snappy writes the page into the chunk's values (SnappyJob::lead)
+    const uint8_t *blk = nullptr;  // GZIP: the block in the caller's file bytes (valid while its chunk is added)
   };
   bool snappy_direct = !(getenv("PQ_SNAPPY_DIRECT") && atoi(getenv("PQ_SNAPPY_DIRECT")) == 0);
   bool dev_snappy = !(getenv("PQ_HOST_SNAPPY") && atoi(getenv("PQ_HOST_SNAPPY")) != 0);
   std::vector<DevSnappy> snappy;
+  // GZIP data pages inflated on the device by k_inflate (PQ_HOST_GZIP=1: on the host; =0: on the
+  // device; default kDevGzipDefault). Pages carry PF_DEV_GZIP and `data` = index into
+  // `gzip` until upload; their output follows the SNAPPY pages' in the decompression region.
+  bool dev_gzip = getenv("PQ_HOST_GZIP") ? atoi(getenv("PQ_HOST_GZIP")) == 0 : kDevGzipDefault;
+  std::vector<DevSnappy> gzip;
+  uint64_t o_gzip = 0, o_gzip_members = 0;
+  int64_t gzip_members = 0;  // members k_inflate decoded (read back at sync)
+  int64_t gzip_host_pages = 0;  // GZIP pages (data and dictionary) handed to the host's inflate
   std::vector<uint8_t> pagebuf;  // the planner's copy of a device-decompressed page's head
   // UNCOMPRESSED pages of chunks added from an on-device page index: the body is copied device to
   // device from the resident file bytes (k_page_gather, at upload) instead of through the stage.
@@ -652,12 +664,23 @@ static int chunk_fail(pqgpu_batch *b, HostChunk &hc, int32_t id, int code, int p
       break;
     }
   }
+  for (const auto &j : b->gzip) {  // the same for GZIP blocks left for k_inflate
+    if (j.page < hc.first_page) continue;
+    std::vector<uint8_t> tmp;
+    if (!Decompress(2, j.blk, j.comp_len, &tmp).ok() || tmp.size() != j.dlen) {
+      code = PQ_ERR_DECOMPRESS;
+      page = (int)(j.page - hc.first_page);
+      m = "decompression failed: gzip: invalid data";
+      break;
+    }
+  }
   set_err(&hc.err, code, id, page, m);
   if (err) *err = hc.err;
   // drop the pages staged for this chunk: the reference returns before any readValues
   b->pages.resize(hc.first_page);
   while (!b->ba_delta.empty() && b->ba_delta.back().page >= hc.first_page) b->ba_delta.pop_back();
   while (!b->snappy.empty() && b->snappy.back().page >= hc.first_page) b->snappy.pop_back();
+  while (!b->gzip.empty() && b->gzip.back().page >= hc.first_page) b->gzip.pop_back();
   while (!b->gathers.empty() && b->gathers.back().page >= hc.first_page) b->gathers.pop_back();
   hc.num_pages = 0;
   return code;
@@ -725,6 +748,15 @@ static int read_block(const uint8_t *file, int64_t flen, int64_t *off, int64_t *
       return PQ_OK;
     }
   }
+  // a GZIP block that starts like a deflate member is left for k_inflate; anything else (and an
+  // empty page) inflates here, with the reference's error
+  if (defer && codec == 2 && usize > 0 && take >= 3 && blk[0] == 0x1f && blk[1] == 0x8b && blk[2] == 8 &&
+      (int64_t)out->size() + usize < (1ll << 31)) {
+    defer->blk = blk;
+    defer->len = take;
+    defer->dlen = usize;
+    return PQ_OK;
+  }
   size_t before = out->size();
   Status st = Decompress(codec, blk, take, out);
   if (!st.ok()) { *msg = st.msg; return st.code; }
@@ -740,9 +772,10 @@ static int read_block(const uint8_t *file, int64_t flen, int64_t *off, int64_t *
 // `ensure(k)`: page bytes [0, k) are readable (a device-decompressed page holds only its head
 // on the host); false if the block is corrupt there.
 static int init_values(const uint8_t *page, int64_t plen, int64_t vstart, uint8_t vk, PageDesc *pd, BaDelta *bd,
-                       std::string *msg, const std::function<bool(int64_t)> &ensure) {
+                       std::string *msg, const std::function<bool(int64_t)> &ensure,
+                       const char *corrupt_msg = "decompression failed: snappy: corrupt input") {
   GoReader r{page + vstart, plen - vstart};
-  auto corrupt = [&] { *msg = "decompression failed: snappy: corrupt input"; return PQ_ERR_DECOMPRESS; };
+  auto corrupt = [&] { *msg = corrupt_msg; return PQ_ERR_DECOMPRESS; };
   pd->val_off = (uint32_t)vstart;
   pd->val_len = (uint32_t)(plen - vstart);
   if (vk == VK_DICT) {  // dictDecoder.init type_dict.go:22-38
@@ -971,6 +1004,7 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
       int e = read_block(file, flen, &off, &count, ph.csize, ph.usize, validate_crc, ph, meta->codec, &block, 0, &msg,
                          nullptr, ixe);
       decomp_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - d0).count();
+      if (meta->codec == 2) b->gzip_host_pages++;
       if (e) return chunk_fail(b, hc, id, e, -1, msg, err);
       hc.has_dict = true;
       hc.dict_count = (uint32_t)ph.dict.num_values;
@@ -1014,8 +1048,11 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
     // init (DELTA_LENGTH / DELTA_BYTE_ARRAY walk every length on the host)
     SnappyDefer sd;
     SnappyPrefix sp;
+    GzipPrefix gzp;
+    const bool is_gzip = meta->codec == 2;
+    const char *corrupt_msg = is_gzip ? "decompression failed: gzip: invalid data" : "decompression failed: snappy: corrupt input";
     bool can_defer = false;
-    if (b->dev_snappy && meta->codec == 1 && (ph.type == 0 ? ph.has_dph : ph.has_dph2)) {
+    if (((b->dev_snappy && meta->codec == 1) || (b->dev_gzip && is_gzip)) && (ph.type == 0 ? ph.has_dph : ph.has_dph2)) {
       uint8_t vk_peek = 0;
       std::string ignored;
       can_defer = pick_vkind(ph.type == 0 ? ph.dph.encoding : ph.dph2.encoding, col->physical_type, col->type_length,
@@ -1035,17 +1072,22 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
       plen = raw_len + sd.dlen;
       if ((int64_t)b->pagebuf.size() < plen + 64) b->pagebuf.resize((size_t)plen + 64);
       if (raw_len) memcpy(b->pagebuf.data(), block.data(), (size_t)raw_len);
-      sp.Init(sd.blk, sd.len, b->pagebuf.data() + raw_len, sd.dlen);
+      if (is_gzip) gzp.Init(sd.blk, sd.len, b->pagebuf.data() + raw_len, sd.dlen);
+      else sp.Init(sd.blk, sd.len, b->pagebuf.data() + raw_len, sd.dlen);
       pg = b->pagebuf.data();
     };
-    auto ensure = [&](int64_t upto) -> bool { return !sd.blk || upto <= raw_len || sp.Extend(upto - raw_len); };
+    auto ensure = [&](int64_t upto) -> bool {
+      if (!sd.blk || upto <= raw_len) return true;
+      return is_gzip ? gzp.Extend(upto - raw_len) : sp.Extend(upto - raw_len);
+    };
     // stage the raw prefix and the block now: a later failure in this chunk checks the block
     auto stage_snappy = [&]() {
       pqgpu_batch::DevSnappy j;
       j.raw_off = stage_append(b, block.data(), (int64_t)block.size());
       j.raw_len = (uint32_t)block.size();
       j.comp_len = (uint32_t)sd.len;
-      j.vlen = (uint32_t)(sp.src - sd.blk);
+      j.vlen = is_gzip ? 0u : (uint32_t)(sp.src - sd.blk);
+      j.blk = sd.blk;
       j.dlen = (uint32_t)sd.dlen;
       j.page = (uint32_t)b->pages.size();
       const int64_t at = (int64_t)(sd.blk - file) - (ix ? ix->file_off : 0);
@@ -1059,10 +1101,11 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
         j.comp_off = stage_append(b, sd.blk, sd.len);
         b->stage.resize(b->stage.size() + 128, 0);  // k_snappy reads up to 70 bytes past the block
       }
-      b->snappy.push_back(j);
+      if (is_gzip) b->gzip.push_back(j);
+      else b->snappy.push_back(j);
     };
     auto corrupt_fail = [&]() {
-      return chunk_fail(b, hc, id, PQ_ERR_DECOMPRESS, pi, "decompression failed: snappy: corrupt input", err);
+      return chunk_fail(b, hc, id, PQ_ERR_DECOMPRESS, pi, corrupt_msg, err);
     };
     if (ph.type == 0) {
       // dataPageReaderV1.init page_v1.go:65-85 then read :87-122
@@ -1076,6 +1119,7 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
       int e = read_block(file, flen, &off, &count, ph.csize, ph.usize, validate_crc, ph, meta->codec, &block, 0, &msg,
                          can_defer ? &sd : nullptr, ixe, want_direct);
       if (!e) bind_page();
+      if (is_gzip && !sd.blk) b->gzip_host_pages++;
       decomp_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - d0).count();
       if (e) return chunk_fail(b, hc, id, e, pi, msg, err);
       if (sd.blk) stage_snappy();
@@ -1105,7 +1149,7 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
         pd.flags |= PF_DEF;
         r.i += take;
       }
-      if ((e = init_values(pg, plen, r.i, vk, &pd, &bd, &msg, ensure))) return chunk_fail(b, hc, id, e, pi, msg, err);
+      if ((e = init_values(pg, plen, r.i, vk, &pd, &bd, &msg, ensure, corrupt_msg))) return chunk_fail(b, hc, id, e, pi, msg, err);
     } else {
       // dataPageReaderV2.read page_v2.go:79-131
       if (!ph.has_dph2) return chunk_fail(b, hc, id, PQ_ERR_INVALID, pi, "null DataPageHeaderV2", err);
@@ -1120,6 +1164,7 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
       e = read_block(file, flen, &off, &count, ph.csize, ph.usize, validate_crc, ph, meta->codec, &block, levels, &msg,
                      can_defer ? &sd : nullptr, ixe, want_direct);
       if (!e) bind_page();
+      if (is_gzip && !sd.blk) b->gzip_host_pages++;
       decomp_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - d0).count();
       if (e) return chunk_fail(b, hc, id, e, pi, msg, err);
       if (sd.blk) stage_snappy();
@@ -1137,7 +1182,7 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
         pd.def_len = (uint32_t)ph.dph2.def_len;
         pd.flags |= PF_DEF;
       }
-      if ((e = init_values(pg, plen, levels, vk, &pd, &bd, &msg, ensure))) return chunk_fail(b, hc, id, e, pi, msg, err);
+      if ((e = init_values(pg, plen, levels, vk, &pd, &bd, &msg, ensure, corrupt_msg))) return chunk_fail(b, hc, id, e, pi, msg, err);
     }
     if (hc.num_slots + pd.num_slots > 0x7fffffffULL)
       return chunk_fail(b, hc, id, PQ_ERR_UNSUPPORTED, pi, "more than 2^31-1 level slots in one chunk", err);
@@ -1148,8 +1193,8 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
       b->ba_delta.push_back(bd);
     }
     if (sd.blk) {  // staged by stage_snappy(); k_snappy writes the page
-      pd.flags |= PF_DEV_SNAPPY;
-      pd.data = b->snappy.size() - 1;  // job index until upload
+      pd.flags |= is_gzip ? PF_DEV_GZIP : PF_DEV_SNAPPY;
+      pd.data = (is_gzip ? b->gzip.size() : b->snappy.size()) - 1;  // job index until upload
     } else if (direct) {  // resident: k_page_gather copies the block at upload
       pd.flags |= PF_DEV_GATHER;
       pd.data = b->gathers.size();  // gather-job index until upload
@@ -1647,7 +1692,7 @@ static int build_and_upload(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   {
     const char *ge = getenv("PQ_SNAPPY_GROUPS");
     const int want = ge ? atoi(ge) : 1;  // (default: off until measured)
-    bool ok = want > 1 && !b->snappy.empty() && (!cf || atoi(cf) != 0) && b->level_pages.empty() &&
+    bool ok = want > 1 && !b->snappy.empty() && b->gzip.empty() && (!cf || atoi(cf) != 0) && b->level_pages.empty() &&
               b->level_pages_bw1.empty() && b->ba_chunks.empty() && nc >= 2;
     for (const auto &hc : b->chunks) ok = ok && hc.col.max_rep == 0 && hc.col.max_def == 0 && !hc.nest;
     for (const auto &it : b->items) ok = ok && it.kind != WI_DELTA_TILE && it.kind != WI_DLENS;
@@ -1784,6 +1829,8 @@ static int build_and_upload(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   b->o_dbg = take(64 * 8);
   b->o_ba_delta = take(b->ba_delta.size() * sizeof(BaDelta));
   b->o_snappy = take(b->snappy.size() * sizeof(SnappyJob));
+  b->o_gzip = take(b->gzip.size() * sizeof(InflateJob));
+  b->o_gzip_members = take(8);
   b->o_gather = take(b->gathers.size() * sizeof(GatherJob));
   b->pba_seg0.push_back((uint32_t)b->pba_seg_page.size());  // [n_pages + 1]
   b->l_pba_pages = take(b->pba_pages.size() * 4);
@@ -1870,6 +1917,11 @@ static int build_and_upload(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
     dec_off[k] = dec;
     if (!b->snappy[k].to_values)  // direct pages need no region of their own
       dec = align_up(dec + align_up((uint64_t)b->snappy[k].raw_len + b->snappy[k].dlen, 16) + 64, 256);
+  }
+  std::vector<uint64_t> inf_off(b->gzip.size());  // then the pages k_inflate writes (same layout)
+  for (size_t k = 0; k < b->gzip.size(); k++) {
+    inf_off[k] = dec;
+    dec = align_up(dec + align_up((uint64_t)b->gzip[k].raw_len + b->gzip[k].dlen, 16) + 64, 256);
   }
   // then the resident UNCOMPRESSED pages k_page_gather copies in (same layout)
   const uint64_t gat_base = align_up(dec_base + dec, 256);
@@ -1991,12 +2043,23 @@ static int build_and_upload(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
       jobs[k].lead = 1 + (uint32_t)(jobs[k].dst & 15);
     }
   }
+  std::vector<InflateJob> ijobs(b->gzip.size());
+  for (size_t k = 0; k < ijobs.size(); k++) {
+    const pqgpu_batch::DevSnappy &j = b->gzip[k];
+    const PageDesc &pd = b->pages[j.page];
+    const uint64_t comp = j.comp_gather >= 0 ? gjobs[(size_t)j.comp_gather].dst : (uint64_t)(b->d_stage + j.comp_off);
+    ijobs[k] = InflateJob{comp, (uint64_t)(b->d_stage + j.raw_off), (uint64_t)(b->d_stage + dec_base + inf_off[k]),
+                          j.comp_len, j.raw_len, j.dlen, pd.chunk, pd.page_in_chunk, 0};
+  }
   std::vector<PageDesc> pages = b->pages;
   for (auto &pd : pages)
     pd.data = (pd.flags & PF_DEV_SNAPPY)   ? jobs[pd.data].dst
+              : (pd.flags & PF_DEV_GZIP)   ? ijobs[pd.data].dst
               : (pd.flags & PF_DEV_GATHER) ? gjobs[pd.data].dst
                                            : (uint64_t)(b->d_stage + pd.data);
   HIPCHECK(hipMemcpyAsync(A + b->o_snappy, jobs.data(), jobs.size() * sizeof(SnappyJob), hipMemcpyHostToDevice, s), err);
+  if (!ijobs.empty())
+    HIPCHECK(hipMemcpyAsync(A + b->o_gzip, ijobs.data(), ijobs.size() * sizeof(InflateJob), hipMemcpyHostToDevice, s), err);
   if (!gjobs.empty()) {
     HIPCHECK(hipMemcpyAsync(A + b->o_gather, gjobs.data(), gjobs.size() * sizeof(GatherJob), hipMemcpyHostToDevice, s),
              err);
@@ -2215,7 +2278,7 @@ static int decode_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   const bool delta_major = b->n_groups == 0 && b->spec && b->n_delta_items > 0 && !any_nest && !b->one_stream &&
                            b->copy_mode == 0 && !b->levels_first && !l.n_scan_pages && !b->n_dict_items &&
                            l.n_items == b->n_delta_items && !pl.n_pages && !l.n_ba_delta && !l.n_copy_items &&
-                           b->ba_chunks.empty() && !l.n_rec_pages && !side;
+                           b->ba_chunks.empty() && !l.n_rec_pages && !side && b->gzip.empty();
   // Dictionary-only schedule (flat REQUIRED dictionary / boolean-RLE columns, value bases known at
   // upload; cfg1): the run scan and the dictionary tiles, two launches on the batch stream and
   // nothing else per decode. k_scan_runs resets its pages' tile tables itself, the dictionary launch
@@ -2223,7 +2286,7 @@ static int decode_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   // schedule); the other per-decode state is written by no kernel of this schedule, so the first
   // decode's reset holds for the later ones.
   const bool lvl_any0 = l.n_level_pages + l.n_level_pages_bw1 + l.n_lv_tiles > 0;
-  const bool dict_only = b->n_groups == 0 && (b->spec || b->bases_known) && b->snappy.empty() && !any_delta && !any_nest && !lvl_any0 &&
+  const bool dict_only = b->n_groups == 0 && (b->spec || b->bases_known) && b->snappy.empty() && b->gzip.empty() && !any_delta && !any_nest && !lvl_any0 &&
                          b->n_dict_items > 0 && l.n_items == b->n_dict_items && l.n_scan_pages > 0 &&
                          !l.n_copy_items && !pl.n_pages && !l.n_ba_delta && b->ba_chunks.empty() && !l.n_rec_pages &&
                          !l.n_base_chunks && !l.n_lf_list && b->copy_mode == 0 && !b->levels_first && !side &&
@@ -2290,6 +2353,14 @@ static int decode_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   } else if (!b->snappy.empty()) {
     HIPCHECK(timed(b, 11, s, b->snappy.size(), [&] {
                return launch_snappy(d, (const SnappyJob *)(A + b->o_snappy), (uint32_t)b->snappy.size(), s);
+             }),
+             err);
+  }
+  if (!b->gzip.empty()) {  // GZIP pages: before every kernel that reads page data, like the SNAPPY ones
+    HIPCHECK(hipMemsetAsync(A + b->o_gzip_members, 0, 8, s), err);
+    HIPCHECK(timed(b, 25, s, b->gzip.size(), [&] {
+               return launch_inflate(d, (const InflateJob *)(A + b->o_gzip), (uint32_t)b->gzip.size(),
+                                     (unsigned long long *)(A + b->o_gzip_members), s);
              }),
              err);
   }
@@ -2590,7 +2661,7 @@ static int decode_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
 }
 
 // Key -> pqgpu_error (see err_key in pq_device.h).
-static void decode_key(uint64_t key, int chunk, pqgpu_error *e) {
+static void decode_key(uint64_t key, int chunk, pqgpu_error *e, int32_t codec) {
   uint32_t phase = (uint32_t)(key >> 62);
   uint32_t page = (uint32_t)((key >> 40) & 0x3fffff);
   uint32_t stage = (uint32_t)((key >> 36) & 15);
@@ -2598,8 +2669,9 @@ static void decode_key(uint64_t key, int chunk, pqgpu_error *e) {
   uint32_t code = (uint32_t)(key & 15);
   static const char *stages[] = {"dictionary", "repetition levels", "definition levels", "values"};
   char msg[200];
-  if (phase == 0 && stage == ST_DECOMP) {  // k_snappy: the page's readPages failure
-    set_err(e, (int)code, chunk, (int)page, "decompression failed: snappy: corrupt input");
+  if (phase == 0 && stage == ST_DECOMP) {  // k_snappy / k_inflate: the page's readPages failure
+    set_err(e, (int)code, chunk, (int)page,
+            codec == 2 ? "decompression failed: gzip: invalid data" : "decompression failed: snappy: corrupt input");
   } else if (phase == 0) {
     snprintf(msg, sizeof(msg), "%s decode failed at entry %u: %s", stages[stage & 3], pos, pqgpu_status_string((int)code));
     set_err(e, (int)code, chunk, -1, msg);
@@ -2652,6 +2724,12 @@ static int sync_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
     ba_tot.resize(nc);
     HIPCHECK(hipMemcpy(ba_tot.data(), A + b->o_ba_totals, (size_t)nc * 8, hipMemcpyDeviceToHost), err);
   }
+  b->gzip_members = 0;
+  if (!b->gzip.empty()) {
+    unsigned long long m = 0;
+    HIPCHECK(hipMemcpy(&m, A + b->o_gzip_members, 8, hipMemcpyDeviceToHost), err);
+    b->gzip_members = (int64_t)m;
+  }
   b->page_vbase_out = vbase;
   b->page_nn_out = nn;
   int first = PQ_OK;
@@ -2662,7 +2740,7 @@ static int sync_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
     HostChunk &hc = b->chunks[c];
     clear_err(&hc.dev_err);
     hc.dev_err.chunk = (int)c;
-    if (!hc.err.code && keys[c] != ~0ull) decode_key(keys[c], (int)c, &hc.dev_err);
+    if (!hc.err.code && keys[c] != ~0ull) decode_key(keys[c], (int)c, &hc.dev_err, hc.meta.codec);
     // a page's readValues error leaves the pages before it decoded (the reference's lazy page
     // reader returns their rows first, data_store.go:236-260); decompression and CRC errors are
     // readPages errors (chunk_reader.go:161-180): nothing of the chunk is returned
@@ -2790,6 +2868,7 @@ static int sync_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   kb[8] = dict_bytes;                                   // k_values_dict: dictionary tiles
   kb[9] = val_bytes - cp_bytes - dl_bytes - dict_bytes;  // k_values: the other LDS kinds
   kb[11] = b->stats.snappy_kernel_bytes;
+  for (const auto &j : b->gzip) kb[25] += (int64_t)j.comp_len + 2 * (int64_t)j.raw_len + j.dlen;
   memcpy(b->slot_bytes, kb, sizeof(kb));
   b->stats.levels_kernel_bytes = lvl_bytes;
   b->stats.values_kernel_bytes = val_bytes;
@@ -3009,6 +3088,9 @@ int pqgpu_batch_reset(pqgpu_batch *b) {
   b->pages.clear();
   b->ba_delta.clear();
   b->snappy.clear();
+  b->gzip.clear();
+  b->gzip_members = 0;
+  b->gzip_host_pages = 0;
   b->gathers.clear();
   b->stage.clear();
   b->uploaded = b->decoded = false;
@@ -3597,6 +3679,16 @@ int pqgpu_batch_debug_counters(pqgpu_batch *b, uint64_t *out64, int reset) {
 
 int pqgpu_batch_stats_get(const pqgpu_batch *b, pqgpu_batch_stats *out) {
   *out = b->stats;
+  return PQ_OK;
+}
+
+int pqgpu_batch_codec_stats(const pqgpu_batch *b, pqgpu_codec_stats *out) {
+  if (!b || !out) return PQ_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  out->gzip_pages = (int64_t)b->gzip.size();
+  out->gzip_host_pages = b->gzip_host_pages;
+  for (const auto &j : b->gzip) out->gzip_kernel_bytes += (int64_t)j.comp_len + 2 * (int64_t)j.raw_len + j.dlen;
+  out->gzip_members = b->gzip_members;
   return PQ_OK;
 }
 

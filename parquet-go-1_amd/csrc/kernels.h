@@ -155,6 +155,8 @@ hipError_t launch_reset(void *z, uint64_t zn, void *f, uint64_t fn, hipStream_t 
 hipError_t launch_ba_delta(const BatchDev &b, const LaunchLists &l, hipStream_t s);      // DLBA / DBA values
 hipError_t launch_dba_gather(const BatchDev &b, const LaunchLists &l, hipStream_t s);    // DBA payloads
 hipError_t launch_snappy(const BatchDev &b, const SnappyJob *jobs, uint32_t njobs, hipStream_t s);  // SNAPPY pages
+hipError_t launch_inflate(const BatchDev &b, const InflateJob *jobs, uint32_t njobs, unsigned long long *members,
+                          hipStream_t s);  // GZIP pages (inflate.hip)
 hipError_t launch_delta_prep(const BatchDev &b, const LaunchLists &l, hipStream_t s);  // walk + sums + prefix
 // PLAIN BYTE_ARRAY pages (plainba.hip): speculative segment walks, verified per page
 struct PbaLists {

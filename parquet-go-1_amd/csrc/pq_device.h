@@ -47,6 +47,7 @@ enum : uint16_t {
                      // values, block size not dividing kDeltaTileVals, > 8 miniblocks): exact scalar path
   PF_DEV_SNAPPY = 32,// host only: `data` is an offset into the device decompression region (k_snappy)
   PF_DEV_GATHER = 64,// host only: `data` is a gather-job index (page body copied from resident file bytes)
+  PF_DEV_GZIP = 128, // host only: `data` is an offset into the device decompression region (k_inflate)
 };
 
 // Error staging key (64 bit, smaller = reported first):
@@ -206,6 +207,20 @@ struct SnappyJob {       // 48 B
                          // == dlen) is written straight into the chunk's values array at its value base,
                          // without the 64-B pad; no k_values item copies it again (the
                          // decompressed body IS the output, page_v1.go:87-122, type_*.go PLAIN)
+};
+// GZIP data page inflated on the device (compress.go:63-76; inflate.hip): the stage (or, for a
+// resident block, its gathered copy) holds the block's gzip members followed by >= 128 zero bytes;
+// k_inflate writes the page at `dst` in the layout k_snappy leaves.
+struct InflateJob {      // 48 B
+  uint64_t src;          // device address of the block (its first member's magic)
+  uint64_t raw;          // device address of the raw prefix (16-B aligned)
+  uint64_t dst;          // device address of the page data (16-B aligned)
+  uint32_t src_len;      // block bytes
+  uint32_t raw_len;
+  uint32_t dlen;         // the page header's uncompressed size less the V2 level bytes
+  uint32_t chunk;
+  uint32_t page_in_chunk;
+  uint32_t pad;
 };
 #ifndef PQ_SNAPPY_RING
 #define PQ_SNAPPY_RING 16384

@@ -75,6 +75,12 @@ class ChunkResult(ctypes.Structure):
                 ("group_entries", ctypes.c_int64 * 8), ("group_validity", ctypes.c_void_p * 8)]
 
 
+class CodecStats(ctypes.Structure):
+    """pqgpu_codec_stats: GZIP data pages by route (gzip_members: after sync)."""
+    _fields_ = [("gzip_pages", ctypes.c_int64), ("gzip_host_pages", ctypes.c_int64),
+                ("gzip_kernel_bytes", ctypes.c_int64), ("gzip_members", ctypes.c_int64)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("num_chunks", ctypes.c_int64), ("num_pages", ctypes.c_int64), ("num_slots", ctypes.c_int64),
                 ("num_values", ctypes.c_int64), ("input_bytes", ctypes.c_int64), ("output_bytes", ctypes.c_int64),
@@ -119,7 +125,7 @@ class PipelineStats(ctypes.Structure):
 
 
 _LIB = None
-TIMER_SLOTS = 25  # PQGPU_TIMER_SLOTS
+TIMER_SLOTS = 26  # PQGPU_TIMER_SLOTS
 ABI_VERSION = 8  # PQGPU_ABI_VERSION in include/pqgpu.h (struct layouts above)
 _EXPORTS = [
     "pqgpu_abi_version", "pqgpu_status_string", "pqgpu_ctx_create", "pqgpu_ctx_destroy", "pqgpu_file_open",
@@ -127,7 +133,7 @@ _EXPORTS = [
     "pqgpu_file_column", "pqgpu_file_chunk_meta", "pqgpu_batch_create", "pqgpu_batch_destroy", "pqgpu_batch_reset",
     "pqgpu_batch_add_chunk", "pqgpu_batch_add_file_chunk", "pqgpu_batch_upload", "pqgpu_batch_decode",
     "pqgpu_batch_sync", "pqgpu_batch_wait", "pqgpu_batch_num_chunks", "pqgpu_batch_chunk_status", "pqgpu_batch_chunk_result",
-    "pqgpu_batch_copy_chunk", "pqgpu_batch_stats_get", "pqgpu_batch_kernel_timing", "pqgpu_batch_kernel_time",
+    "pqgpu_batch_copy_chunk", "pqgpu_batch_stats_get", "pqgpu_batch_codec_stats", "pqgpu_batch_kernel_timing", "pqgpu_batch_kernel_time",
     "pqgpu_batch_debug_counters", "pqgpu_batch_kernel_slot", "pqgpu_batch_chunk_pages", "pqgpu_batch_kernel_bytes",
     "pqgpu_copy", "pqgpu_pipeline_create", "pqgpu_pipeline_next", "pqgpu_pipeline_release", "pqgpu_pipeline_stats_get",
     "pqgpu_pipeline_destroy", "pqgpu_batch_copy_nested", "pqgpu_page_index_build", "pqgpu_page_index_chunk",
@@ -174,6 +180,7 @@ def lib():
         "pqgpu_batch_chunk_result": ([P, ctypes.c_int32, ctypes.POINTER(ChunkResult), E], ctypes.c_int),
         "pqgpu_batch_copy_chunk": ([P, ctypes.c_int32, P, P, P, P, P, P, P, E], ctypes.c_int),
         "pqgpu_batch_stats_get": ([P, ctypes.POINTER(BatchStats)], ctypes.c_int),
+        "pqgpu_batch_codec_stats": ([P, ctypes.POINTER(CodecStats)], ctypes.c_int),
         "pqgpu_batch_kernel_timing": ([P, ctypes.c_int], ctypes.c_int),
         "pqgpu_batch_debug_counters": ([P, P, ctypes.c_int], ctypes.c_int),
         "pqgpu_batch_kernel_time": ([P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
@@ -441,6 +448,12 @@ class Batch:
     def stats(self):
         s = BatchStats()
         lib().pqgpu_batch_stats_get(self._h, ctypes.byref(s))
+        return s
+
+    def codec_stats(self):
+        """GZIP data pages inflated by k_inflate / on the host, k_inflate's bytes, members (after sync)."""
+        s = CodecStats()
+        lib().pqgpu_batch_codec_stats(self._h, ctypes.byref(s))
         return s
 
     def debug_counters(self, reset=True):
