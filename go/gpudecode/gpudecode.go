@@ -339,6 +339,45 @@ func (b *Batch) Wait() error {
 	return toErr(C.pqgpu_batch_wait(b.b, nil, &e), &e)
 }
 
+// ArrowLayout is pqgpu_arrow_layout: the sizes of a chunk's buffers in Arrow's
+// physical layout (every *Bytes a multiple of 64; include/pqgpu.h, "Arrow export").
+type ArrowLayout struct {
+	Length, NullCount                                  int64
+	ValuesBytes, OffsetsBytes, ValidityBytes, DataBytes int64
+	Tiles                                              int64
+	PhysicalType, ValueWidth                           int32
+}
+
+// ArrowBuffers is pqgpu_arrow_buffers: caller-owned device destinations, 16-byte
+// aligned and sized from the ArrowLayout; nil skips that buffer. They are device
+// addresses, never Go memory.
+type ArrowBuffers struct {
+	Values, Offsets, Validity, Data unsafe.Pointer
+}
+
+// ArrowLayout describes chunk id after Sync. For a chunk that failed in a page
+// the decoded prefix is described and the chunk's error returned with it.
+func (b *Batch) ArrowLayout(id int32) (ArrowLayout, error) {
+	var l C.pqgpu_arrow_layout
+	var e C.pqgpu_error
+	rc := C.pqgpu_batch_arrow_layout(b.b, C.int32_t(id), &l, &e)
+	return ArrowLayout{int64(l.length), int64(l.null_count), int64(l.values_bytes), int64(l.offsets_bytes),
+		int64(l.validity_bytes), int64(l.data_bytes), int64(l.tiles), int32(l.physical_type),
+		int32(l.value_width)}, toErr(rc, &e)
+}
+
+// ExportArrow writes chunk id into dst in Arrow's physical layout
+// (pqgpu_batch_export_arrow), asynchronously on stream (a hipStream_t; nil: the
+// context's stream). Wait covers it; the next Decode or reset of the batch must
+// not start before. A chunk that failed in a page exports its decoded prefix
+// and returns the chunk's error.
+func (b *Batch) ExportArrow(id int32, dst ArrowBuffers, stream unsafe.Pointer) error {
+	var e C.pqgpu_error
+	d := C.pqgpu_arrow_buffers{values: dst.Values, offsets: (*C.int32_t)(dst.Offsets),
+		validity: (*C.uint8_t)(dst.Validity), data: (*C.uint8_t)(dst.Data)}
+	return toErr(C.pqgpu_batch_export_arrow(b.b, C.int32_t(id), &d, stream, &e), &e)
+}
+
 // CodecStats counts the batch's GZIP data pages by route: inflated on the
 // device by k_inflate or on the host (pqgpu_batch_codec_stats). Members is
 // valid after Sync.

@@ -357,6 +357,76 @@ int pqgpu_batch_copy_group(const pqgpu_batch *b, int32_t chunk_id, int32_t group
  * decoded without error; PQ_ERR_ARG when their paths share no ancestor
  * structure consistently (e.g. leaves of different files). */
 int pqgpu_batch_share_ancestors(pqgpu_batch *b, int32_t chunk_a, int32_t chunk_b, int32_t *equal, pqgpu_error *err);
+
+/* ---- Arrow export ------------------------------------------------------
+ * pqgpu_chunk_result describes a column as the reference's readValues does:
+ * the non-null values packed, one offset per value, one byte per BOOLEAN.
+ * An Arrow array has one value slot per array slot, one offset per slot and
+ * bit-packed booleans. pqgpu_batch_export_arrow writes a decoded chunk into
+ * caller-owned device buffers in that layout (k_arrow_rank / k_arrow_expand,
+ * DESIGN.md section 13); the chunk result itself is not changed.
+ *
+ * The array's slots are the chunk's elements (num_elements, bitmap
+ * element_validity) when the result has nest_levels > 0 -- the leaf under
+ * lvl_offsets / lvl_validity -- and its level slots (num_slots, bitmap
+ * validity; no bitmap when max_def == 0) otherwise. With valid(i) = bit i of
+ * that bitmap and rank(i) = the number of valid slots before i:
+ *   values    INT32/FLOAT 4 B, INT64/DOUBLE 8 B, INT96 12 B, FIXED_LEN_BYTE_ARRAY
+ *             type_length B: values[i] = valid(i) ? result.values[rank(i)] : 0
+ *             (bit copies). BOOLEAN: a bitmap, bit i = valid(i) ?
+ *             result.values[rank(i)] & 1 : 0.
+ *   offsets   BYTE_ARRAY: int32[length + 1], offsets[i] = result.offsets[rank(i)]
+ *             (a null slot is empty; offsets[length] = payload_bytes).
+ *   validity  bit i = valid(i) for i < length (length one-bits without a bitmap).
+ *   data      BYTE_ARRAY: a copy of result.payload (a caller that passes NULL
+ *             uses result.payload in place).
+ * Every byte of every buffer up to its size in the layout is written: null
+ * slots, validity bits at and past length and the padding are zero, so two
+ * exports of one decode are byte-identical. */
+typedef struct {
+  int64_t length;          /* Arrow array length: num_elements when the chunk result has nest_levels > 0,
+                              else num_slots (for a failed chunk with a decoded prefix: the prefix) */
+  int64_t null_count;      /* length - num_values */
+  int64_t values_bytes;    /* fixed width: length * width; BOOLEAN: ceil(length/8); BYTE_ARRAY: 0 */
+  int64_t offsets_bytes;   /* BYTE_ARRAY: (length + 1) * 4, else 0 */
+  int64_t validity_bytes;  /* ceil(length/8), at least 64: 0 is never reported, a caller may still pass NULL */
+  int64_t data_bytes;      /* BYTE_ARRAY payload bytes (unchanged by the export), else 0 */
+  int64_t tiles;           /* rank tiles the export will run (0 when null_count == 0) */
+  int32_t physical_type, value_width;  /* width 0 for BOOLEAN (bit-packed) and BYTE_ARRAY */
+} pqgpu_arrow_layout;      /* every *_bytes is rounded up to a multiple of 64 */
+
+typedef struct { void *values; int32_t *offsets; uint8_t *validity; uint8_t *data; } pqgpu_arrow_buffers;
+
+/* The layout of a `length`-slot array with `num_values` non-null values: pure
+ * host arithmetic, usable without a GPU. PQ_ERR_ARG for an unknown type, a
+ * negative argument, num_values > length, or FIXED_LEN_BYTE_ARRAY with
+ * type_length <= 0. */
+int pqgpu_arrow_layout_for(int32_t physical_type, int32_t type_length, int64_t length, int64_t num_values,
+                           int64_t payload_bytes, pqgpu_arrow_layout *out);
+/* The layout of chunk `chunk_id`, after pqgpu_batch_sync (PQ_ERR_ARG before
+ * it, or for a bad id). A chunk that failed in a page: as pqgpu_batch_copy_chunk,
+ * the decoded prefix is described and the chunk's error returned; without a
+ * prefix *out is zeroed and the error alone returned. */
+int pqgpu_batch_arrow_layout(const pqgpu_batch *b, int32_t chunk_id, pqgpu_arrow_layout *out, pqgpu_error *err);
+/* Export chunk `chunk_id` into `dst`. Runs after pqgpu_batch_sync (PQ_ERR_ARG
+ * before it, or for a bad id; PQ_ERR_HIP on a plan-only batch) and is
+ * asynchronous on `stream`; pqgpu_batch_wait(b, stream) covers it. The next
+ * decode, upload or reset of the batch must not start while an export is in
+ * flight: the export reads the batch's arena.
+ * Destinations are caller-owned device memory, 16-byte aligned (else
+ * PQ_ERR_ARG), at least the layout's byte counts and disjoint from the
+ * batch's memory. Any pointer may be NULL to skip that buffer (NULL `values`
+ * on a fixed-width chunk: a validity-only export).
+ * A chunk that failed in a page: the decoded prefix is exported and the
+ * chunk's error returned; without a prefix nothing is written.
+ * The per-tile rank bases live in device memory of the batch, one region per
+ * chunk, allocated by the chunk's first export and kept until
+ * pqgpu_batch_reset or pqgpu_batch_destroy: a repeated export allocates
+ * nothing, and exports of different chunks may run on different streams (two
+ * exports of one chunk share its region: keep them on one stream). */
+int pqgpu_batch_export_arrow(pqgpu_batch *b, int32_t chunk_id, const pqgpu_arrow_buffers *dst, void *stream,
+                             pqgpu_error *err);
+
 int pqgpu_batch_stats_get(const pqgpu_batch *b, pqgpu_batch_stats *out);
 /* GZIP data pages of the batch by route (valid after the chunks are added; gzip_members after sync). */
 typedef struct {

@@ -276,6 +276,10 @@ struct HostChunk {
   // results after sync
   int64_t nn = 0, records = 0, payload_bytes = 0;
   pqgpu_error dev_err{};
+  // pqgpu_batch_export_arrow: the chunk's rank scratch (bases[tiles + 1] u64, then counts[tiles]
+  // u32), allocated by its first export and kept until the chunk set changes or the batch goes
+  void *arrow_scratch = nullptr;
+  size_t arrow_scratch_cap = 0;
 };
 
 // Value-decoder choice: getValuesDecoder chunk_reader.go:106-159.
@@ -640,6 +644,7 @@ struct pqgpu_batch {
   bool debug_stamps = getenv("PQ_DEBUG_STAMPS") && atoi(getenv("PQ_DEBUG_STAMPS")) != 0;
   std::vector<ChunkDesc> chunk_desc;
   bool uploaded = false, decoded = false;
+  bool results_ready = false;  // synced since the last decode: chunk results are what the device holds
   pqgpu_batch_stats stats{};
   KernelTimer timer;
   int64_t slot_bytes[PQGPU_TIMER_SLOTS] = {0};  // algorithmic bytes per launch of each timer slot
@@ -960,6 +965,7 @@ static int add_chunk_impl(pqgpu_batch *b, const uint8_t *file, int64_t flen, con
   hc.first_page = (uint32_t)b->pages.size();
   hc.value_width = value_width_of(col->physical_type, col->type_length);
   b->uploaded = false;
+  b->results_ready = false;
   clear_err(err);
   if (meta->has_file_path) return chunk_fail(b, hc, id, PQ_ERR_UNSUPPORTED, -1, "nyi: data is in another file", err);
   if (meta->physical_type != col->physical_type)
@@ -2256,6 +2262,7 @@ static hipError_t join_deferred(pqgpu_batch *b, hipStream_t s) {
 }
 
 static int decode_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
+  b->results_ready = false;
   if (!b->uploaded) {
     int e = build_and_upload(b, s, err);
     if (e) return e;
@@ -2760,7 +2767,8 @@ static int sync_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
     }
     if (!hc.err.code && hc.sync_err && !hc.dev_err.code)
       set_err(&hc.dev_err, PQ_ERR_UNSUPPORTED, (int)c, -1, "BYTE_ARRAY chunk payload exceeds 2 GiB");
-    if (!ba_tot.empty() && hc.value_width == 0) hc.payload_bytes = (int64_t)ba_tot[c];
+    // (a chunk without byte-array tiles -- no values at all -- has no total written for it)
+    if (!ba_tot.empty() && hc.value_width == 0) hc.payload_bytes = b->chunk_desc[c].ba_ntiles ? (int64_t)ba_tot[c] : 0;
     for (uint32_t k = 0; k < PQGPU_MAX_NEST; k++)
       hc.num_lists[k] = k < hc.nest ? (int64_t)nest_tot[(size_t)c * kNestCnt + k] : 0;
     hc.num_elems = hc.nest ? (int64_t)nest_tot[(size_t)c * kNestCnt + hc.nest] : 0;
@@ -2877,6 +2885,7 @@ static int sync_impl(pqgpu_batch *b, hipStream_t s, pqgpu_error *err) {
   b->stats.num_slots = slots;
   b->stats.num_values = values;
   b->timer.resolve();
+  b->results_ready = true;
   return first;
 }
 
@@ -3042,6 +3051,9 @@ static void free_payloads(pqgpu_batch *b) {
     hc.payload = nullptr;
     hc.payload_cap = 0;
     hc.payload_own = false;
+    if (hc.arrow_scratch) (void)hipFree(hc.arrow_scratch);  // (the chunks go with a reset or the batch)
+    hc.arrow_scratch = nullptr;
+    hc.arrow_scratch_cap = 0;
   }
 }
 
@@ -3093,7 +3105,7 @@ int pqgpu_batch_reset(pqgpu_batch *b) {
   b->gzip_host_pages = 0;
   b->gathers.clear();
   b->stage.clear();
-  b->uploaded = b->decoded = false;
+  b->uploaded = b->decoded = b->results_ready = false;
   b->force_serial = spec_disabled();
   b->stats = pqgpu_batch_stats{};
   return PQ_OK;
@@ -3636,6 +3648,182 @@ int pqgpu_batch_copy_chunk(const pqgpu_batch *b, int32_t id, void *values, int32
   HIPCHECK(cp(rep_levels, r.rep_levels, (size_t)r.num_slots), err);
   HIPCHECK(cp(validity, r.validity, (size_t)((r.num_slots + 31) / 32) * 4), err);
   HIPCHECK(cp(list_offsets, r.list_offsets, r.list_offsets ? (size_t)(r.num_records + 1) * 4 : 0), err);
+  return e;
+}
+
+// ---- Arrow export (arrow.hip) ----------------------------------------------------------------
+static int64_t round64(int64_t n) { return (n + 63) & ~(int64_t)63; }
+
+int pqgpu_arrow_layout_for(int32_t physical_type, int32_t type_length, int64_t length, int64_t num_values,
+                           int64_t payload_bytes, pqgpu_arrow_layout *out) {
+  if (!out) return PQ_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  if (physical_type < PQ_BOOLEAN || physical_type > PQ_FIXED_LEN_BYTE_ARRAY || length < 0 || num_values < 0 ||
+      num_values > length || payload_bytes < 0)
+    return PQ_ERR_ARG;
+  if (physical_type == PQ_FIXED_LEN_BYTE_ARRAY && type_length <= 0) return PQ_ERR_ARG;
+  const int w = physical_type == PQ_BOOLEAN ? 0 : value_width_of(physical_type, type_length);
+  if (w > 0 && length > (INT64_MAX - 63) / w) return PQ_ERR_ARG;
+  out->length = length;
+  out->null_count = length - num_values;
+  out->physical_type = physical_type;
+  out->value_width = w;
+  if (physical_type == PQ_BYTE_ARRAY) {
+    out->offsets_bytes = round64((length + 1) * 4);
+    out->data_bytes = round64(payload_bytes);
+  } else {
+    out->values_bytes = round64(w ? length * w : (length + 7) / 8);
+  }
+  out->validity_bytes = std::max<int64_t>(64, round64((length + 7) / 8));
+  out->tiles = out->null_count ? (length + kArrowTileHost - 1) / kArrowTileHost : 0;
+  return PQ_OK;
+}
+
+// The chunk as the export sees it: the array's length, its bitmap (NULL: none) and the compacted
+// sources. Returns the chunk's error beside a decoded prefix, the error alone (*has = false)
+// without one.
+struct ArrowSource {
+  pqgpu_chunk_result r;
+  int64_t length = 0;
+  const uint32_t *bitmap = nullptr;
+};
+static int arrow_source(const pqgpu_batch *b, int32_t id, ArrowSource *a, bool *has, pqgpu_error *err) {
+  *has = false;
+  clear_err(err);
+  if (!b || id < 0 || id >= (int32_t)b->chunks.size()) {
+    set_err(err, PQ_ERR_ARG, -1, -1, "chunk id out of range");
+    return PQ_ERR_ARG;
+  }
+  if (!b->results_ready) {
+    set_err(err, PQ_ERR_ARG, id, -1, "batch not decoded and synced");
+    return PQ_ERR_ARG;
+  }
+  const int e = pqgpu_batch_chunk_result(b, id, &a->r, err);
+  if (e && !a->r.num_slots) return e;  // nothing decoded (as pqgpu_batch_copy_chunk)
+  const bool nested = a->r.nest_levels > 0;
+  a->length = nested ? a->r.num_elements : a->r.num_slots;
+  a->bitmap = nested ? a->r.element_validity : a->r.validity;
+  if (a->r.num_values > a->length || (!a->bitmap && a->r.num_values != a->length)) {
+    set_err(err, PQ_ERR_INVALID, id, -1, "chunk result: value count does not match its slots");
+    return PQ_ERR_INVALID;
+  }
+  if (!a->r.num_values) a->r.payload_bytes = 0;  // (a chunk without pages reports no payload total)
+  // the compacted sources the kernels read must exist wherever a value does
+  const bool ba = a->r.physical_type == PQ_BYTE_ARRAY;
+  if ((ba && a->length && !a->r.offsets) || (!ba && a->r.num_values && !a->r.values) ||
+      (ba && a->r.payload_bytes && !a->r.payload)) {
+    set_err(err, PQ_ERR_INVALID, id, -1, "chunk result: missing value arrays");
+    return PQ_ERR_INVALID;
+  }
+  *has = true;
+  return e;
+}
+
+int pqgpu_batch_arrow_layout(const pqgpu_batch *b, int32_t id, pqgpu_arrow_layout *out, pqgpu_error *err) {
+  if (!out) {
+    set_err(err, PQ_ERR_ARG, id, -1, "null argument");
+    return PQ_ERR_ARG;
+  }
+  memset(out, 0, sizeof(*out));
+  ArrowSource a;
+  bool has;
+  const int e = arrow_source(b, id, &a, &has, err);
+  if (!has) return e;
+  const HostChunk &hc = b->chunks[(size_t)id];
+  if (pqgpu_arrow_layout_for(hc.col.physical_type, hc.col.type_length, a.length, a.r.num_values, a.r.payload_bytes, out)) {
+    set_err(err, PQ_ERR_ARG, id, -1, "chunk has no Arrow layout");
+    return PQ_ERR_ARG;
+  }
+  return e;
+}
+
+int pqgpu_batch_export_arrow(pqgpu_batch *b, int32_t id, const pqgpu_arrow_buffers *dst, void *stream,
+                             pqgpu_error *err) {
+  clear_err(err);
+  if (!b || !dst || id < 0 || id >= (int32_t)b->chunks.size()) {
+    set_err(err, PQ_ERR_ARG, -1, -1, !b || !dst ? "null argument" : "chunk id out of range");
+    return PQ_ERR_ARG;
+  }
+  NEED_CTX(b, err);
+  pqgpu_arrow_layout L;
+  ArrowSource a;
+  bool has;
+  const int e = arrow_source(b, id, &a, &has, err);
+  if (!has) return e;
+  HostChunk &hc = b->chunks[(size_t)id];
+  if (pqgpu_arrow_layout_for(hc.col.physical_type, hc.col.type_length, a.length, a.r.num_values, a.r.payload_bytes, &L)) {
+    set_err(err, PQ_ERR_ARG, id, -1, "chunk has no Arrow layout");
+    return PQ_ERR_ARG;
+  }
+  for (const void *p : {(const void *)dst->values, (const void *)dst->offsets, (const void *)dst->validity,
+                        (const void *)dst->data})
+    if ((uintptr_t)p & 15) {
+      set_err(err, PQ_ERR_ARG, id, -1, "destination not 16-byte aligned");
+      return PQ_ERR_ARG;
+    }
+  const pqgpu_error chunk_err = err ? *err : pqgpu_error{};  // (HIPCHECK below would overwrite it)
+  HIPCHECK(hipSetDevice(b->ctx->device), err);
+  const hipStream_t s = pick_stream(b, stream);
+  const uint64_t len = (uint64_t)a.length, nv = (uint64_t)a.r.num_values;
+  const int t = L.physical_type;
+  // zero a destination's bytes [from, to)
+  auto zero = [&](void *p, int64_t from, int64_t to) -> hipError_t {
+    return to > from ? hipMemsetAsync((uint8_t *)p + from, 0, (size_t)(to - from), s) : hipSuccess;
+  };
+  if (dst->validity) HIPCHECK(launch_arrow_validity(a.bitmap, len, dst->validity, (uint64_t)L.validity_bytes, s), err);
+  const bool want_values = t == PQ_BYTE_ARRAY ? dst->offsets != nullptr : dst->values != nullptr;
+  const uint64_t *bases = nullptr;
+  if (want_values && L.tiles) {  // the rank pass: per-tile bases in the chunk's own scratch
+    const size_t need = (size_t)(L.tiles + 1) * 8 + (size_t)L.tiles * 4;
+    if (hc.arrow_scratch_cap < need) {
+      if (hc.arrow_scratch) (void)hipFree(hc.arrow_scratch);
+      hc.arrow_scratch = nullptr;
+      hc.arrow_scratch_cap = 0;
+      if (hipMalloc(&hc.arrow_scratch, need) != hipSuccess) {
+        hc.arrow_scratch = nullptr;
+        set_err(err, PQ_ERR_NOMEM, id, -1, "arrow export: rank scratch allocation failed");
+        return PQ_ERR_NOMEM;
+      }
+      hc.arrow_scratch_cap = need;
+    }
+    uint64_t *bs = (uint64_t *)hc.arrow_scratch;
+    HIPCHECK(launch_arrow_rank(a.bitmap, len, (uint32_t)L.tiles, (uint32_t *)(bs + L.tiles + 1), bs, s), err);
+    bases = bs;
+  }
+  // no null slot: the bitmap (if any) is all ones below length, rank(i) = i
+  const uint32_t *bm = L.tiles ? a.bitmap : nullptr;
+  if (t == PQ_BYTE_ARRAY) {
+    if (dst->offsets) {
+      if (!nv) {  // no value, no payload: every offset is 0 (a chunk without pages has no offsets[0] written)
+        HIPCHECK(zero(dst->offsets, 0, L.offsets_bytes), err);
+      } else if (!L.tiles) {
+        HIPCHECK(hipMemcpyAsync(dst->offsets, a.r.offsets, (size_t)(len + 1) * 4, hipMemcpyDeviceToDevice, s), err);
+        HIPCHECK(zero(dst->offsets, (int64_t)(len + 1) * 4, L.offsets_bytes), err);
+      } else {
+        HIPCHECK(launch_arrow_expand(ARROW_OFFSETS, bm, len, bases, a.r.offsets, nv, 4, dst->offsets,
+                                     (uint64_t)L.offsets_bytes, s), err);
+      }
+    }
+    if (dst->data) {
+      if (a.r.payload_bytes)
+        HIPCHECK(hipMemcpyAsync(dst->data, a.r.payload, (size_t)a.r.payload_bytes, hipMemcpyDeviceToDevice, s), err);
+      HIPCHECK(zero(dst->data, a.r.payload_bytes, L.data_bytes), err);
+    }
+  } else if (dst->values && len) {
+    const int w = L.value_width;
+    if (t == PQ_BOOLEAN) {
+      HIPCHECK(launch_arrow_expand(ARROW_BOOL, bm, len, bases, a.r.values, nv, 1, dst->values, (uint64_t)L.values_bytes, s), err);
+    } else if (!L.tiles) {
+      HIPCHECK(hipMemcpyAsync(dst->values, a.r.values, (size_t)len * (size_t)w, hipMemcpyDeviceToDevice, s), err);
+      HIPCHECK(zero(dst->values, (int64_t)len * w, L.values_bytes), err);
+    } else {
+      const ArrowKind k = (w == 4 && t != PQ_FIXED_LEN_BYTE_ARRAY)   ? ARROW_FIXED4
+                          : (w == 8 && t != PQ_FIXED_LEN_BYTE_ARRAY) ? ARROW_FIXED8
+                                                                     : ARROW_BYTES;
+      HIPCHECK(launch_arrow_expand(k, bm, len, bases, a.r.values, nv, (uint32_t)w, dst->values, (uint64_t)L.values_bytes, s), err);
+    }
+  }
+  if (err) *err = chunk_err;
   return e;
 }
 

@@ -180,6 +180,22 @@ hipError_t launch_page_walk(const uint8_t *buf, int64_t len, int64_t file_off, c
                             uint32_t nchunks, uint4 *res, PageIxEntry *table, uint32_t *table_n, uint32_t table_cap,
                             int validate_crc, uint32_t gen, hipStream_t s);
 hipError_t launch_page_gather(const GatherJob *jobs, uint32_t njobs, hipStream_t s);
+// Arrow export (arrow.hip): a decoded chunk's compacted values expanded to one slot per array slot.
+// bm: the chunk's bitmap (NULL = every slot valid), read for ceil(length / 32) words, the last one
+// masked by length. Every destination is 16-B aligned and written over [0, dst_bytes) exactly
+// (dst_bytes a multiple of 64).
+constexpr uint32_t kArrowTileHost = 8192;  // T: slots per rank / expand tile (arrow.hip kArT)
+constexpr uint32_t kArrowScanHost = 1024;  // S: tile counts per step of k_arrow_scan (arrow.hip kArS)
+enum ArrowKind { ARROW_FIXED4, ARROW_FIXED8, ARROW_OFFSETS, ARROW_BOOL, ARROW_BYTES };
+// counts[tiles] = valid slots of each tile, bases[tiles + 1] = their exclusive sums and the total
+hipError_t launch_arrow_rank(const uint32_t *bm, uint64_t length, uint32_t tiles, uint32_t *counts, uint64_t *bases,
+                             hipStream_t s);
+// bases == NULL: no slot is null (rank(i) = i). nv: source values (ARROW_OFFSETS: src has nv + 1
+// entries); width: bytes per value (ARROW_BYTES)
+hipError_t launch_arrow_expand(ArrowKind kind, const uint32_t *bm, uint64_t length, const uint64_t *bases,
+                               const void *src, uint64_t nv, uint32_t width, void *dst, uint64_t dst_bytes,
+                               hipStream_t s);
+hipError_t launch_arrow_validity(const uint32_t *bm, uint64_t length, void *dst, uint64_t dst_bytes, hipStream_t s);
 
 // Names of the kernels, for the timing hook.
 extern const char *kValuesKernelName;

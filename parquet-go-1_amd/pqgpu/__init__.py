@@ -81,6 +81,22 @@ class CodecStats(ctypes.Structure):
                 ("gzip_kernel_bytes", ctypes.c_int64), ("gzip_members", ctypes.c_int64)]
 
 
+class ArrowLayout(ctypes.Structure):
+    """pqgpu_arrow_layout: sizes of a chunk's Arrow buffers (every *_bytes a multiple of 64)."""
+    _fields_ = [("length", ctypes.c_int64), ("null_count", ctypes.c_int64), ("values_bytes", ctypes.c_int64),
+                ("offsets_bytes", ctypes.c_int64), ("validity_bytes", ctypes.c_int64), ("data_bytes", ctypes.c_int64),
+                ("tiles", ctypes.c_int64), ("physical_type", ctypes.c_int32), ("value_width", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ArrowBuffers(ctypes.Structure):
+    """pqgpu_arrow_buffers: caller-owned device destinations (16-byte aligned; 0 skips one)."""
+    _fields_ = [("values", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("validity", ctypes.c_void_p),
+                ("data", ctypes.c_void_p)]
+
+
 class BatchStats(ctypes.Structure):
     _fields_ = [("num_chunks", ctypes.c_int64), ("num_pages", ctypes.c_int64), ("num_slots", ctypes.c_int64),
                 ("num_values", ctypes.c_int64), ("input_bytes", ctypes.c_int64), ("output_bytes", ctypes.c_int64),
@@ -140,6 +156,7 @@ _EXPORTS = [
     "pqgpu_page_index_page", "pqgpu_page_index_walk_ms", "pqgpu_page_index_stats", "pqgpu_page_index_destroy", "pqgpu_parse_page_header",
     "pqgpu_batch_add_indexed_chunk", "pqgpu_batch_add_indexed_file_chunk", "pqgpu_dev_alloc", "pqgpu_dev_free",
     "pqgpu_batch_copy_group", "pqgpu_batch_share_ancestors",
+    "pqgpu_arrow_layout_for", "pqgpu_batch_arrow_layout", "pqgpu_batch_export_arrow",
 ]
 
 
@@ -216,6 +233,10 @@ def lib():
                                                 ctypes.POINTER(ctypes.c_int32), E], ctypes.c_int),
         "pqgpu_dev_alloc": ([P, ctypes.c_size_t, ctypes.POINTER(P), E], ctypes.c_int),
         "pqgpu_dev_free": ([P, P], None),
+        "pqgpu_arrow_layout_for": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.POINTER(ArrowLayout)], ctypes.c_int),
+        "pqgpu_batch_arrow_layout": ([P, ctypes.c_int32, ctypes.POINTER(ArrowLayout), E], ctypes.c_int),
+        "pqgpu_batch_export_arrow": ([P, ctypes.c_int32, ctypes.POINTER(ArrowBuffers), P, E], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -570,6 +591,33 @@ class Batch:
                               np.unpackbits(gv.view(np.uint8), bitorder="little")[:n]))
         return cd
 
+    def arrow_layout(self, cid, partial=False):
+        """pqgpu_batch_arrow_layout: the ArrowLayout of chunk `cid` after sync() (raises DecodeError
+        if the chunk failed, or before a sync). partial=True returns (ArrowLayout of the pages decoded
+        before a failing page, or None; DecodeError or None), as result(partial=True)."""
+        lay, err = ArrowLayout(), Error()
+        rc = lib().pqgpu_batch_arrow_layout(self._h, cid, ctypes.byref(lay), ctypes.byref(err))
+        if partial:
+            e = DecodeError(err) if rc else None
+            return (None if rc and not lay.validity_bytes else lay), e
+        _check(rc, err)
+        return lay
+
+    def export_arrow(self, cid, values=0, offsets=0, validity=0, data=0, stream=None, partial=False):
+        """pqgpu_batch_export_arrow: write chunk `cid` in Arrow's physical layout into device buffers
+        given as integer addresses (as pqgpu.copy; 16-byte aligned, sized from arrow_layout(cid), 0
+        skips that buffer). Asynchronous on `stream` (an integer hipStream_t; None: the context's
+        stream): wait() covers it, and the next decode or reset must not start before. Raises
+        DecodeError if the chunk failed; partial=True returns the DecodeError (or None) instead, with
+        the pages decoded before a failing page exported."""
+        dst = ArrowBuffers(values or None, offsets or None, validity or None, data or None)
+        err = Error()
+        rc = lib().pqgpu_batch_export_arrow(self._h, cid, ctypes.byref(dst), ctypes.c_void_p(stream) if stream else None,
+                                            ctypes.byref(err))
+        if partial:
+            return DecodeError(err) if rc else None
+        _check(rc, err)
+
     def share_ancestors(self, cid_a, cid_b):
         """pqgpu_batch_share_ancestors: True when the two leaves' common ancestors (list levels and
         OPTIONAL groups on the shared path prefix) decoded identically; chunk b's result then carries
@@ -653,13 +701,14 @@ class DeviceBuffer:
     """Device memory on libpqgpu's runtime holding `data` (pqgpu_dev_alloc + pqgpu_copy)."""
 
     def __init__(self, ctx, data=None, pad=64, src_addr=None, size=None):
-        """`data` (bytes-like), or `size` bytes at host address `src_addr` (no intermediate copy)."""
-        self.ctx, self.size = ctx, (len(data) if src_addr is None else size)
+        """`data` (bytes-like), or `size` bytes at host address `src_addr` (no intermediate copy), or
+        `size` bytes left as allocated (neither given)."""
+        self.ctx, self.size = ctx, (len(data) if src_addr is None and data is not None else size)
         self.ptr = ctypes.c_void_p()
         _live_indexes.add(self)
         err = Error()
         _check(lib().pqgpu_dev_alloc(ctx._h, self.size + pad, ctypes.byref(self.ptr), ctypes.byref(err)), err)
-        if self.size:
+        if self.size and (data is not None or src_addr is not None):
             if src_addr is None:
                 src = ctypes.create_string_buffer(bytes(data), self.size)
                 src_addr = ctypes.addressof(src)
@@ -750,6 +799,16 @@ class PageIndex:
             self.close()
         except Exception:
             pass
+
+
+def arrow_layout_for(physical_type, type_length, length, num_values, payload_bytes=0):
+    """pqgpu_arrow_layout_for: the ArrowLayout of a `length`-slot array with `num_values` non-null
+    values (host arithmetic, no GPU); ValueError for arguments the library rejects (PQ_ERR_ARG)."""
+    lay = ArrowLayout()
+    rc = lib().pqgpu_arrow_layout_for(physical_type, type_length, length, num_values, payload_bytes, ctypes.byref(lay))
+    if rc:
+        raise ValueError(f"pqgpu_arrow_layout_for: {ERROR_NAMES.get(rc, rc)}")
+    return lay
 
 
 def copy(ctx, dst, src, nbytes):
