@@ -126,7 +126,8 @@ hipError_t launch_scan_runs(const BatchDev &b, const LaunchLists &l, hipStream_t
 hipError_t launch_scan_slots(const BatchDev &b, const LaunchLists &l, hipStream_t s);  // k_scan_runs + k_dict_slots
 hipError_t launch_values(const BatchDev &b, const LaunchLists &l, hipStream_t s);
 hipError_t launch_values_copy(const BatchDev &b, const LaunchLists &l, hipStream_t s);
-hipError_t launch_values_delta(const BatchDev &b, const WorkItem *items, uint32_t n, hipStream_t s);  // DELTA items only
+// DELTA items only; tiles: the batch has WI_DELTA_TILE items (the entry with the tile stage in its LDS)
+hipError_t launch_values_delta(const BatchDev &b, const WorkItem *items, uint32_t n, bool tiles, hipStream_t s);
 // WI_DICT2 (grouped) items [0, n_pair), then WI_DICT items [n_pair, n)
 hipError_t launch_values_dict(const BatchDev &b, const WorkItem *items, uint32_t n_pair, uint32_t n, hipStream_t s);
 // byte-array outputs (bytearray.hip): per-tile payload sums, per-chunk scan of the tile sums,

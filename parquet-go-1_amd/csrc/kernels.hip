@@ -3545,15 +3545,34 @@ DEV void do_delta_tile(const BatchDev &b, const WorkItem &wi, const PageDesc &pd
 // ---------------------------------------------------------------------------
 struct DeltaPageLDS {
   uint32_t win[kDeltaWinLoad / 4 + 8];  // stream bytes [win0, win0 + kDeltaWinLoad + 32)
-  uint32_t hpos[kDeltaMaxBlk];          // header position of each walked block
-  uint32_t ppos[kDeltaMaxBlk];          // payload position
+  uint32_t pos[kDeltaMaxBlk];           // header position of each walked block; the parse puts the
+                                        // block's payload position in its place (same thread)
   int64_t md[kDeltaMaxBlk];
   uint64_t wd[kDeltaMaxBlk];            // miniblock widths, 8 bits each
   uint64_t wsum[2][4];                  // per-wave batch totals (double-buffered by batch parity)
-  uint4 xpose[4][128];                  // per-wave output transpose (2 KiB of output at a time)
+  uint4 xpose[4][64];                   // per-wave output transpose (1 KiB of output at a time)
   unsigned long long stop;              // (value position << 4 | class) of the first error
   uint32_t nb, next;
 };
+// LDS budget of the cfg2 step. k_values_delta runs kDeltaWgPerCu workgroups per CU when alone
+// (waves_per_eu 5, 88 VGPRs), and in the DELTA-major schedule about kSegWavesPerCu k_levels_seg
+// waves per CU are resident beside it (host.cpp seg_grid); 5 x 88 + 72 VGPRs are one SIMD's file, so
+// LDS decides whether the fifth workgroup stays. Slot-time model: alone the launch keeps 5 slots
+// per CU busy for T_alone; a workgroup slot lost for the time T_lv the level waves are resident
+// costs T = (5 T_alone + T_lv) / 5 (0.287 -> 0.329 ms when both structures took 20 KB).
+// Both sizes are rounded up to the allocation granule: the profiler's LDS_Block_Size rounds to
+// 512 B (19,504 -> 19,968 in the kernel trace of the earlier layout), the compiler's figure for
+// gfx950's 160 KiB LDS is 1,280 B (320 dwords); the budget holds for either.
+constexpr uint32_t kLdsPerCu = 160 * 1024;
+constexpr uint32_t kLdsGranuleTrace = 512, kLdsGranuleAlloc = 1280;
+constexpr uint32_t kDeltaWgPerCu = 5, kSegWavesPerCu = 4;
+constexpr uint32_t lds_round_up(uint32_t bytes, uint32_t granule) { return (bytes + granule - 1) / granule * granule; }
+constexpr bool delta_beside_levels_fits(uint32_t granule) {
+  return kDeltaWgPerCu * lds_round_up(sizeof(DeltaPageLDS), granule) +
+             kSegWavesPerCu * lds_round_up(sizeof(LevelSegLDS), granule) <= kLdsPerCu;
+}
+static_assert(delta_beside_levels_fits(kLdsGranuleTrace) && delta_beside_levels_fits(kLdsGranuleAlloc),
+              "five k_values_delta workgroups and four k_levels_seg waves no longer share a CU's LDS");
 
 union ValuesLDS {
   DeltaTileLDS dtile;        // WI_DELTA_TILE
@@ -3701,14 +3720,14 @@ DEV void do_delta_page(const BatchDev &b, const DeltaStream &ds, uint32_t nn, De
           const uint32_t bj = lane == 0 ? bl : (Pj + bl <= lim ? delta_blk_len_lane(L.win, win0, (uint32_t)Pj, mbc, g8) : 0u);
           const uint64_t nb = ~__ballot(bj == bl);
           const uint32_t m = min(nb ? (uint32_t)__builtin_ctzll(nb) : 64u, kmax - k);
-          if (lane < m) L.hpos[k + lane] = (uint32_t)Pj;
+          if (lane < m) L.pos[k + lane] = (uint32_t)Pj;
           k += m;
           p += m * bl;
         }
         // one block by the exact rules (or the end of the walk)
         if (k >= kmax) break;
         if (p >= n) {  // next() reads this block's header at EOF: the parse reports it
-          if (lane == 0) L.hpos[k] = p;
+          if (lane == 0) L.pos[k] = p;
           k++;
           break;
         }
@@ -3717,13 +3736,13 @@ DEV void do_delta_page(const BatchDev &b, const DeltaStream &ds, uint32_t nn, De
         uint64_t wdv;
         uint32_t hl;
         if (sgpr(delta_hdr_parse(L.win, (uint32_t)win0, s, n, p, is64, mbc, &md, &wdv, &hl))) {
-          if (lane == 0) L.hpos[k] = p;  // header error: the parse reports it
+          if (lane == 0) L.pos[k] = p;  // header error: the parse reports it
           k++;
           break;
         }
         const uint32_t bl = sgpr(hl + g8 * bytesum64_swar(wdv));
         if (!tail && (int64_t)p + bl + 24 > lend && k > 0) break;  // block not staged whole
-        if (lane == 0) L.hpos[k] = p;
+        if (lane == 0) L.pos[k] = p;
         k++;
         if ((uint64_t)p + bl > n) break;  // the stream ends inside this block: the parse reports it
         p += bl;
@@ -3742,7 +3761,7 @@ DEV void do_delta_page(const BatchDev &b, const DeltaStream &ds, uint32_t nn, De
     if (more) fetch(nwin0);  // lands during the parse and the batches
     // ---- 3. parse: thread k re-reads block k's header exactly, finds its first unreadable group
     if (tid < nb) {
-      const uint32_t p = L.hpos[tid], j = blk + tid;
+      const uint32_t p = L.pos[tid], j = blk + tid;
       int64_t md = 0;
       uint64_t wdv = 0;
       uint32_t hl = 0;
@@ -3767,7 +3786,7 @@ DEV void do_delta_page(const BatchDev &b, const DeltaStream &ds, uint32_t nn, De
       }
       L.md[tid] = md;
       L.wd[tid] = wdv;
-      L.ppos[tid] = p + hl;
+      L.pos[tid] = p + hl;
       if (key != ~0ull) atomicMin(&L.stop, key);
     }
     wg_barrier();
@@ -3794,7 +3813,7 @@ DEV void do_delta_page(const BatchDev &b, const DeltaStream &ds, uint32_t nn, De
         const uint64_t wdv = L.wd[k];
         const uint32_t w = (uint32_t)(wdv >> (8 * m)) & 0xffu;
         const uint64_t below = m ? (wdv & ((1ull << (8 * m)) - 1ull)) : 0ull;
-        const uint32_t goff = L.ppos[k] + g8 * bytesum64(below) + (o / 8) * w;
+        const uint32_t goff = L.pos[k] + g8 * bytesum64(below) + (o / 8) * w;
         delta_unpack8_lds(L.win, win0, goff, w, is64, L.md[k], d);
 #pragma unroll
         for (int q = 0; q < 8; q++) sum += d[q];
@@ -3819,43 +3838,86 @@ DEV void do_delta_page(const BatchDev &b, const DeltaStream &ds, uint32_t nn, De
       if (PQ_ABLATE(b, 0)) {  // diagnostic: no stores (kept live by an impossible condition)
         if (out[7] == 0x0123456789abcdefull && valid) ((uint64_t *)ds.out)[d0] = out[0];
       } else if (__ballot(valid && d0 + 8 <= stop) == ~0ull) {
-        // the wave's 64 groups are 512 consecutive values: transpose through LDS so that every
-        // store instruction writes 1 KiB contiguous (16 B per lane) instead of 64 B-strided pieces.
-        // The output leaves in 2 KiB halves (int64: lanes 0-31, then lanes 32-63; int32: one half,
-        // every lane). Piece e (16 B) of a half is held by lane e / vw as its piece e % vw; it sits
-        // in LDS slot xsw(e): the piece index within the lane is XOR-swizzled with lane bits so that
-        // the 16-B writes of 16 (int64) / 8 (int32) consecutive lanes cover all 64 banks (lanes
-        // 64 B / 32 B apart would otherwise meet in the same banks, 4- / 2-way).
+        // the wave's 64 groups are 512 consecutive values: transpose so that every store instruction
+        // writes 1 KiB contiguous (16 B per lane) instead of 64 B-strided pieces. A lane holds vw = 4
+        // (int64) / 2 (int32) pieces of 16 B, its group's 64 / 32 B; the output leaves in vw passes of
+        // 1 KiB (16 / 32 lanes' groups), each through the wave's 1 KiB LDS buffer.
+        // 1. In registers, the wave's 64 / vw-lane rows x vw pieces are block-transposed by lane-row
+        //    swaps (v_permlane32_swap, then v_permlane16_swap for int64): afterwards register set h of
+        //    lane l holds piece l / (64 / vw) of lane (64 / vw) * h + l % (64 / vw), so every lane has
+        //    one piece of every pass and a pass is ONE full-wave 16-B LDS write (exec-masked writes of
+        //    a quarter of the lanes cost the LDS store path a whole instruction each: measured
+        //    k_values_delta alone 0.285 -> 0.294 ms).
+        // 2. Pass h: lane l writes its piece e = vw * (l % (64 / vw)) + l / (64 / vw) to LDS slot
+        //    xsw(e), reads slot xsw(l) and stores it at byte 1024 h + 16 l. xsw XORs the piece index
+        //    within a lane with lane bits: a 16-B LDS write is served in groups of 8 consecutive lanes
+        //    over 32 banks (8 slots), and lanes 64 B / 32 B apart would meet in the same banks 4- /
+        //    2-way; with bits 1-2 (int64) / bit 2 (int32) of the source lane folded in the 8 lanes of a
+        //    group cover the 8 slots (int64 folds bit 3 in as well: 16 consecutive lanes then cover 16
+        //    slots of 64 banks). The reads permute inside aligned groups of vw slots: conflict-free.
+        // The same wave's LDS accesses execute in order: no wait between a pass's read and the next
+        // pass's write.
         uint4 *xw = L.xpose[wv];
         auto xsw = [&](uint32_t e) -> uint32_t {
-          return is64 ? (e & ~3u) | ((e ^ (e >> 4)) & 3u) : (e & ~1u) | ((e ^ (e >> 4)) & 1u);
+          return is64 ? (e & ~3u) | ((e ^ (e >> 3) ^ (e >> 5)) & 3u) : (e & ~1u) | ((e ^ (e >> 3)) & 1u);
+        };
+        auto swap32 = [](uint32_t &x, uint32_t &y) {  // rows 2-3 of x <-> rows 0-1 of y (a row: 16 lanes)
+          const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+          x = r[0];
+          y = r[1];
+        };
+        auto swap16 = [](uint32_t &x, uint32_t &y) {  // rows 1, 3 of x <-> rows 0, 2 of y
+          const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+          x = r[0];
+          y = r[1];
         };
         const uint32_t wd0 = rdlane(d0, 0);
-        const uint32_t nhalf = is64 ? 2u : 1u;
-        for (uint32_t h = 0; h < nhalf; h++) {
-          if (is64) {
-            if ((lane >> 5) == h) {
-              const uint32_t l32 = lane & 31u;
+        uint8_t *dst0 = ds.out + (uint64_t)wd0 * (is64 ? 8 : 4) + 16u * lane;
+        uint32_t w[4][4];
+        uint4 r[4];
+        if (is64) {
 #pragma unroll
-              for (int q = 0; q < 4; q++)
-                xw[xsw(l32 * 4 + q)] = make_uint4((uint32_t)out[2 * q], (uint32_t)(out[2 * q] >> 32),
-                                                  (uint32_t)out[2 * q + 1], (uint32_t)(out[2 * q + 1] >> 32));
-            }
-          } else {
-            xw[xsw(lane * 2)] = make_uint4((uint32_t)out[0], (uint32_t)out[1], (uint32_t)out[2], (uint32_t)out[3]);
-            xw[xsw(lane * 2 + 1)] = make_uint4((uint32_t)out[4], (uint32_t)out[5], (uint32_t)out[6], (uint32_t)out[7]);
+          for (int q = 0; q < 4; q++) {
+            w[q][0] = (uint32_t)out[2 * q];
+            w[q][1] = (uint32_t)(out[2 * q] >> 32);
+            w[q][2] = (uint32_t)out[2 * q + 1];
+            w[q][3] = (uint32_t)(out[2 * q + 1] >> 32);
           }
-          asm volatile("" ::: "memory");  // same wave: LDS executes its accesses in order
-          uint8_t *dst0 = ds.out + (uint64_t)wd0 * (is64 ? 8 : 4) + 2048u * h;
-          if (al16) {
-            uint4 *dst = (uint4 *)dst0;
 #pragma unroll
-            for (uint32_t q = 0; q < 2; q++) cp_st16(&dst[q * 64 + lane], xw[xsw(q * 64 + lane)]);
-          } else {  // 4-B aligned output: the same pieces, unaligned 16-B stores
+          for (int k = 0; k < 4; k++) { swap32(w[0][k], w[2][k]); swap32(w[1][k], w[3][k]); }
 #pragma unroll
-            for (uint32_t q = 0; q < 2; q++) cp_st16_ua(dst0 + 16u * (q * 64 + lane), xw[xsw(q * 64 + lane)]);
+          for (int k = 0; k < 4; k++) { swap16(w[0][k], w[1][k]); swap16(w[2][k], w[3][k]); }
+          const uint32_t se = xsw((lane & 15u) * 4 + (lane >> 4)), sl = xsw(lane);
+#pragma unroll
+          for (int h = 0; h < 4; h++) {
+            xw[se] = make_uint4(w[h][0], w[h][1], w[h][2], w[h][3]);
+            asm volatile("" ::: "memory");
+            r[h] = xw[sl];
+            asm volatile("" ::: "memory");
           }
-          asm volatile("" ::: "memory");  // this half's LDS reads precede the next half's writes
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; k++) { w[0][k] = (uint32_t)out[k]; w[1][k] = (uint32_t)out[4 + k]; }
+#pragma unroll
+          for (int k = 0; k < 4; k++) swap32(w[0][k], w[1][k]);
+          const uint32_t se = xsw((lane & 31u) * 2 + (lane >> 5)), sl = xsw(lane);
+#pragma unroll
+          for (int h = 0; h < 2; h++) {
+            xw[se] = make_uint4(w[h][0], w[h][1], w[h][2], w[h][3]);
+            asm volatile("" ::: "memory");
+            r[h] = xw[sl];
+            asm volatile("" ::: "memory");
+          }
+        }
+        const uint32_t npass = is64 ? 4u : 2u;
+        if (al16) {
+#pragma unroll
+          for (uint32_t h = 0; h < 4; h++)
+            if (h < npass) cp_st16((uint4 *)(dst0 + 1024u * h), r[h]);
+        } else {  // 4-B aligned output: the same pieces, unaligned 16-B stores
+#pragma unroll
+          for (uint32_t h = 0; h < 4; h++)
+            if (h < npass) cp_st16_ua(dst0 + 1024u * h, r[h]);
         }
       } else if (valid) {
         if (d0 + 8 <= stop && al16) {
@@ -3965,7 +4027,7 @@ DEV void do_delta_slow(const BatchDev &b, const DeltaStream &ds, uint32_t nn) {
 }
 
 // PLAIN / BOOLEAN copies: no LDS, so their workgroups fit on a CU beside the DELTA pages'
-// (39 KB of LDS each) and the level kernels' instead of queueing behind them.
+// (sizeof(DeltaPageLDS), ~15 KB of LDS each) and the level kernels' instead of queueing behind them.
 __global__ void __launch_bounds__(256) k_values_copy(BatchDev b_in, const WorkItem *items) {
   const BatchDev b = global_view(b_in);
   const WorkItem wi = gp(items)[blockIdx.x];
@@ -3981,6 +4043,11 @@ __global__ void __launch_bounds__(256) k_values_copy(BatchDev b_in, const WorkIt
 // first and the bandwidth-bound copies fill the CUs around them): the kernel's registers and LDS
 // are the DELTA decoder's, not the maximum over every work-item kind (dictionary tiles stay in
 // k_values).
+// Two entries: k_values_delta reserves the page decoder's LDS alone (the LDS budget asserted beside
+// DeltaPageLDS counts on it) and takes every batch without DELTA tiles; a batch with tiles
+// (PQ_DELTA_TILED=1) goes to
+// k_values_delta_tiled, whose LDS is the union with the tile stage. A tile that reaches the entry
+// without the stage is reported (PQ_ERR_UNSUPPORTED), never decoded.
 union DeltaLDS {
   DeltaTileLDS dtile;
   DeltaPageLDS dpage;
@@ -3988,7 +4055,8 @@ union DeltaLDS {
 #ifndef PQ_DELTA_WPE
 #define PQ_DELTA_WPE 5
 #endif
-DEV void values_delta(BatchDev b_in, const WorkItem *items, DeltaLDS &lds) {
+template <bool kTiles>
+DEV void values_delta(BatchDev b_in, const WorkItem *items, DeltaPageLDS &dpage, DeltaTileLDS *dtile) {
   const BatchDev b = global_view(b_in);
   if (blockIdx.x == 0 && b.err_next)  // (DELTA-major decodes: the next decode's keys, on this stream)
     for (uint32_t c = threadIdx.x; c < b.nchunks; c += blockDim.x) gp(b.err_next)[c] = ~0ull;
@@ -3998,15 +4066,25 @@ DEV void values_delta(BatchDev b_in, const WorkItem *items, DeltaLDS &lds) {
   const uint32_t nn = b.page_nn_v[wi.page];
   switch (wi.kind) {
     case WI_DELTA: do_delta_slow(b, page_stream(b, wi, pd, cd), nn); break;
-    case WI_DELTA_TILE: do_delta_tile(b, wi, pd, cd, nn, lds.dtile.scan, lds.dtile.stage); break;
-    case WI_DELTA_PAGE: do_delta_page(b, page_stream(b, wi, pd, cd), nn, lds.dpage); break;
+    case WI_DELTA_TILE:
+      if constexpr (kTiles) {
+        do_delta_tile(b, wi, pd, cd, nn, dtile->scan, dtile->stage);
+      } else {  // (workgroup-uniform) launch_values_delta sends batches with tiles to the other entry
+        if (threadIdx.x == 0) report(b, pd.chunk, 1, pd.page_in_chunk, ST_VALUES, wi.v0, PQ_ERR_UNSUPPORTED);
+      }
+      break;
+    case WI_DELTA_PAGE: do_delta_page(b, page_stream(b, wi, pd, cd), nn, dpage); break;
     case WI_PLAIN: do_plain<PQ_FUSED_COPY_U>(b, wi, pd, cd, nn); break;  // fused copies (registers to spare: more in flight)
     case WI_BOOL: do_bool(b, wi, pd, cd, nn); break;
   }
 }
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PQ_DELTA_WPE))) k_values_delta(BatchDev b_in, const WorkItem *items) {
+  __shared__ DeltaPageLDS lds;
+  values_delta<false>(b_in, items, lds, nullptr);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PQ_DELTA_WPE))) k_values_delta_tiled(BatchDev b_in, const WorkItem *items) {
   __shared__ DeltaLDS lds;
-  values_delta(b_in, items, lds);
+  values_delta<true>(b_in, items, lds.dpage, &lds.dtile);
 }
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_values(BatchDev b_in, const WorkItem *items) {
@@ -4800,9 +4878,10 @@ hipError_t launch_values_dict(const BatchDev &b, const WorkItem *items, uint32_t
   if (n > n_pair) hipLaunchKernelGGL(k_values_dict, dim3(n - n_pair), dim3(256), 0, s, b, items + n_pair);
   return hipGetLastError();
 }
-hipError_t launch_values_delta(const BatchDev &b, const WorkItem *items, uint32_t n, hipStream_t s) {
+hipError_t launch_values_delta(const BatchDev &b, const WorkItem *items, uint32_t n, bool tiles, hipStream_t s) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_values_delta, dim3(n), dim3(256), 0, s, b, items);
+  if (tiles) hipLaunchKernelGGL(k_values_delta_tiled, dim3(n), dim3(256), 0, s, b, items);
+  else hipLaunchKernelGGL(k_values_delta, dim3(n), dim3(256), 0, s, b, items);
   return hipGetLastError();
 }
 hipError_t launch_values_copy(const BatchDev &b, const LaunchLists &l, hipStream_t s) {
